@@ -7,7 +7,13 @@ the reference's trained weights), Darknet detector of record (yolov4-tiny-aider-
 run at 608x608; /255 fused), YOLO decode (fused into the head convs) and per-image NMS
 (conf 0.3, IoU 0.4, detect.py defaults).  Frames are resident in HBM before timing.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the result line (metric,
+  value, unit, higher_is_better, dtype, ms_per_step, latencies, configuration).  --full adds
+  the legs that take runs of their own after the timed region: roofline, h2d, cpu_baseline
+  (below; their --roofline-steps / --h2d-steps / --cpu-baseline / --cpu-seconds options only
+  act with --full).  --dump-outputs DIR writes the arrays the last timed step returned
+  (logits, probs, io, det, idx, count) as DIR/<name>.npy, see dump_outputs().
   N>1: `python bench.py --gpus N` starts N ranks itself (fresh child processes of this
        script, one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, before any GPU
        call; rank 0's JSON line is the output, a failing rank fails the run), or
@@ -23,7 +29,7 @@ Each rank replays the step as one hipGraph per input buffer (TwoStagePipeline
 graphs=True); the steps cycle over --rotate distinct frame batches so no step
 re-reads the previous step's frames from the 256 MB Infinity Cache.
 
-Prints ONE JSON line on rank 0 (value = frames/s over all ranks), with
+Prints ONE JSON line on rank 0 (value = frames/s over all ranks), and with --full
   roofline:     the dominant kernel (largest summed device time), its algorithmic FLOP
                 per launch / its average launch time from hipEvents recorded on its
                 launch stream around every detector launch, over --roofline-steps eager
@@ -67,7 +73,13 @@ def parse():
                     help="launcher self-test (no GPU): the ranks join a gloo group and rank 0 prints one JSON "
                          "line with every rank's launch environment")
     ap.add_argument("--dry-fail-rank", type=int, default=-1, help="(--dry-run) this rank exits with status 3")
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure after the timed steps: the per-launch "
+                         "roofline (--roofline-steps), the PCIe-inclusive rate (--h2d-steps) and the CPU oracle "
+                         "baseline (--cpu-baseline); without it those options are ignored")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=64, help="global frames per step (sharded over the ranks)")
     ap.add_argument("--per-gpu-batch", type=int, default=0,
@@ -100,12 +112,15 @@ def parse():
                          "pipeline k %% inflight (own handles, buffers and ONE stream), so consecutive batches "
                          "run concurrently and fill the CUs one batch's low-occupancy kernels leave idle")
     ap.add_argument("--roofline-steps", type=int, default=20,
-                    help="eager steps with per-launch hipEvents after the timed region (0: no roofline)")
-    ap.add_argument("--h2d-steps", type=int, default=20, help="PCIe-inclusive steps (0: skip)")
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="0 disables the CPU oracle leg")
+                    help="(--full) eager steps with per-launch hipEvents after the timed region (0: no roofline)")
+    ap.add_argument("--h2d-steps", type=int, default=20, help="(--full) PCIe-inclusive steps (0: skip)")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="(--full) 0 disables the CPU oracle leg")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
-                    help="CPU oracle leg: time chunks of 16 frames until this much CPU time has passed")
-    return ap.parse_args()
+                    help="(--full) CPU oracle leg: time chunks of 16 frames until this much CPU time has passed")
+    args = ap.parse_args()
+    if not args.full:  # a plain run does only what its headline figure needs
+        args.roofline_steps, args.h2d_steps, args.cpu_baseline = 0, 0, 0
+    return args
 
 
 def free_port():
@@ -420,6 +435,39 @@ def make_frames(args, first, count, dev):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, parts, has_cls, has_det):
+    """--dump-outputs: what a caller of the timed path received from its last timed step, as
+    <path>/<name>.npy.  `parts`: the output views of every rank's shard in rank order (one
+    rank: the pipeline's own views, with io; several: the records rank 0 gathered), joined
+    along the frame axis.  logits, probs, io and det are written as float32, idx and count
+    (int32) as float64.  The kernels leave det / idx rows at and past count[b] unwritten (a
+    caller reads det[b, :count[b]]): those rows are written as zeros, so two builds compare
+    output for output.  At most DUMP_LIMIT_BYTES in all: an array that does not fit the rest of
+    the budget is written as a fixed sample, <name>.npy = its flattened values at the sorted
+    positions <name>_positions.npy (float64; numpy default_rng(0), the same from run to run)."""
+    names = (["logits", "probs"] if has_cls else []) + (["io", "det", "idx", "count"] if has_det else [])
+    arrs = {k: np.concatenate([p[k].detach().cpu().numpy() for p in parts]) for k in names if k in parts[0]}
+    if has_det:
+        past = np.arange(arrs["det"].shape[1])[None, :] >= arrs["count"][:, None]
+        arrs["det"][past] = 0
+        arrs["idx"][past] = 0
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_LIMIT_BYTES
+    for k in sorted(arrs, key=lambda k: arrs[k].size):  # the small arrays whole, first
+        a = arrs[k].astype(np.float32 if arrs[k].dtype == np.float32 else np.float64)
+        if a.nbytes > left:
+            m = left // (a.itemsize + 8)
+            pos = np.unique(np.random.default_rng(0).integers(0, a.size, m))
+            np.save(os.path.join(path, k + "_positions.npy"), pos.astype(np.float64))
+            a = a.reshape(-1)[pos]
+            left -= 8 * pos.size
+        np.save(os.path.join(path, k + ".npy"), a)
+        left -= a.nbytes
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -505,6 +553,12 @@ def main():
         from rtdm.pipeline import unpack_record
         last = gathered[(args.steps - 1) % len(pipes)]  # the buffer of the last timed step's pipeline
         counts = torch.cat([unpack_record(last[r], pipe, b)["count"].cpu() for r in range(world)])
+    if args.dump_outputs and rank == 0:
+        if world > 1:
+            from rtdm.pipeline import unpack_record
+            last = gathered[(args.steps - 1) % len(pipes)]
+        dump_outputs(args.dump_outputs, [out] if world == 1 else [unpack_record(last[r], pipe, b) for r in range(world)],
+                     args.classifier != "none", det is not None)
 
     # ---- roofline: per-launch hipEvents on the detector's launch streams, eager steps ----
     if det is None:

@@ -180,17 +180,18 @@ def test_yolo_acff_stream_from_reference_state_dict():
 
 
 
-REF_WEIGHTS = "/root/reference/code/disaster_detection/weights"
+REF_WEIGHTS = os.path.join(ROOT, "tests", "golden", "pickles")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_WEIGHTS), reason="reference checkpoints not present")
 @pytest.mark.parametrize("model,pickle_name", [("squeeze-ernet", "Squeeze-ernet-92f1score.pt"),
                                                ("squeeze-redconv", "Squeeze-ernet-redconv92acc.pt"),
                                                ("ernet", "ernet-96f1scor.pt")])
 def test_full_module_pickle_loads_allowlisted(model, pickle_name, cls_weights):
     """The reference's full-module pickles load through torch.load(weights_only=True) with
     the allowlist (no code from the file runs) and give the same tensors as the state-dict
-    checkpoints (*-state_dict.pt are bit-identical to these)."""
+    checkpoints (*-state_dict.pt are bit-identical to these).  The files are
+    the reference's weights/<pickle_name>, stored under tests/golden/pickles; ernet-96f1scor.pt
+    has its zip members (the same bytes) deflated, which keeps it under 1 MiB."""
     from rtdm.classifier import build_model, read_weights
     sd = read_weights(os.path.join(REF_WEIGHTS, pickle_name))
     ref = cls_weights[model]
@@ -323,3 +324,61 @@ def test_bench_world_size_must_match_gpus():
     assert r.returncode != 0 and "WORLD_SIZE=2 but --gpus 4" in r.stderr
     r = _bench(["--dry-run"])  # no --gpus, no launcher: one rank
     assert r.returncode == 0 and '"n_gpus": 1' in r.stdout
+
+
+def test_bench_plain_run_skips_the_extra_legs(monkeypatch):
+    """Without --full the roofline, h2d and CPU-baseline legs are off whatever their options
+    say; --full leaves them as given.  --steps is the number of timed steps."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--h2d-steps", "5"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert (a.roofline_steps, a.h2d_steps, a.cpu_baseline) == (0, 0, 0)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--h2d-steps", "5", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert (a.roofline_steps, a.h2d_steps, a.cpu_baseline, a.dump_outputs) == (20, 5, 1, "d")
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.dump_outputs: the shards joined in rank order, float32 / float64 arrays, det and idx
+    rows at and past count zeroed, and under a byte budget the same seeded sample every time."""
+    import bench
+    rng = np.random.default_rng(5)
+    parts, count = [], [[1, 3], [0, 4]]
+    for c in count:
+        parts.append({"logits": torch.from_numpy(rng.standard_normal((2, 5)).astype(np.float32)),
+                      "probs": torch.from_numpy(rng.random((2, 5)).astype(np.float32)),
+                      "io": torch.from_numpy(rng.random((2, 9, 7)).astype(np.float32)),
+                      "det": torch.from_numpy(rng.random((2, 4, 6)).astype(np.float32) + 1),
+                      "idx": torch.from_numpy(rng.integers(1, 9, (2, 4, 2)).astype(np.int32)),
+                      "count": torch.tensor(c, dtype=torch.int32),
+                      "record": torch.zeros(3), "ws": torch.zeros(3, dtype=torch.uint8)})
+    ref = {k: np.concatenate([p[k].numpy() for p in parts]) for k in ("logits", "probs", "io", "det", "idx", "count")}
+    d = tmp_path / "a"
+    bench.dump_outputs(str(d), parts, True, True)
+    assert sorted(os.listdir(d)) == ["count.npy", "det.npy", "idx.npy", "io.npy", "logits.npy", "probs.npy"]
+    got = {k: np.load(d / (k + ".npy")) for k in ref}
+    for k in ("logits", "probs", "io"):
+        assert got[k].dtype == np.float32 and np.array_equal(got[k], ref[k]), k
+    assert got["det"].dtype == np.float32 and got["idx"].dtype == np.float64 and got["count"].dtype == np.float64
+    assert np.array_equal(got["count"], [1, 3, 0, 4])
+    for b, c in enumerate([1, 3, 0, 4]):
+        assert np.array_equal(got["det"][b, :c], ref["det"][b, :c]) and not got["det"][b, c:].any()
+        assert np.array_equal(got["idx"][b, :c], ref["idx"][b, :c]) and not got["idx"][b, c:].any()
+    assert all(np.array_equal(p["det"].numpy(), ref["det"][2 * i:2 * i + 2]) for i, p in enumerate(parts))  # inputs intact
+    # classification only: no detector arrays
+    bench.dump_outputs(str(tmp_path / "c"), [{k: p[k] for k in ("logits", "probs", "record")} for p in parts], True, False)
+    assert sorted(os.listdir(tmp_path / "c")) == ["logits.npy", "probs.npy"]
+    # a budget the largest array (io, 252 floats) does not fit: a fixed sample of it, all else whole
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1400)
+    for name in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / name), parts, True, True)
+    s1 = {f: np.load(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")}
+    s2 = {f: np.load(tmp_path / "s2" / f) for f in os.listdir(tmp_path / "s2")}
+    assert sorted(s1) == sorted(list(f + ".npy" for f in ref) + ["io_positions.npy"])
+    assert all(np.array_equal(s1[f], s2[f]) for f in s1)
+    assert sum(v.nbytes for v in s1.values()) <= 1400
+    pos = s1["io_positions.npy"].astype(np.int64)
+    assert 0 < pos.size < 252 and np.all(np.diff(pos) > 0)
+    assert np.array_equal(s1["io.npy"], ref["io"].reshape(-1)[pos])
+    assert np.array_equal(s1["det.npy"], got["det"])
