@@ -346,6 +346,10 @@ rtdm_status rtdm_resize_linear(const uint8_t* frames, int n, int in_h, int in_w,
  * IDCT, fancy upsampling, YCbCr -> RGB), bit-exact with libjpeg-turbo's default
  * decompression (JDCT_ISLOW, do_fancy_upsampling), i.e. with what cv2.imread and Pillow
  * return.  Progressive / arithmetic / 12-bit streams: supported = 0 and RTDM_E_UNSUPPORTED.
+ * Other 3-component sampling layouts (4:4:0, 4:1:1, ...): supported = 0 as well; the entropy
+ * decode still takes them, rtdm_jpeg_reconstruct returns RTDM_E_UNSUPPORTED.  Malformed
+ * streams (an over-subscribed Huffman table, a scan naming a Huffman table above 3, truncated
+ * headers) are RTDM_E_INVALID.
  *
  * rtdm_jpeg_info_get: geometry from the headers (no entropy decode).
  * rtdm_jpeg_entropy_decode: coef [nblocks][64] int16 (host memory, component c's block
@@ -367,6 +371,84 @@ rtdm_status rtdm_jpeg_entropy_decode(const uint8_t* data, int64_t len, int16_t* 
 int64_t rtdm_jpeg_workspace_bytes(const rtdm_jpeg_info* info);
 rtdm_status rtdm_jpeg_reconstruct(const int16_t* coef, const uint16_t* qt, const rtdm_jpeg_info* info, uint8_t* planes,
                                   int64_t planes_bytes, uint8_t* rgb, int64_t pitch, int bgr, void* stream);
+
+/* ---- batched JPEG ingest (a folder of files: detect.py, aider-predict.py, the mAP harness) ----
+ * The same decode for n streams at once: headers planned in one call, the Huffman stage on
+ * host threads, ONE host-to-device copy and TWO kernel launches per batch whatever the mix
+ * of sizes and sampling layouts.  Coefficients, tables and pixels are bit-identical to the
+ * single-image entry points above.
+ *
+ * All of a batch's host-side data lives in one staging buffer the caller owns (pinned
+ * memory, so that one async copy carries it): [descriptors | qt | coef], at byte offsets 0,
+ * layout.qt_offset and layout.coef_offset, layout.staging_bytes in all.
+ *
+ * rtdm_jpeg_batch_plan: headers only (no entropy decode).  Per image i: info[i] (as
+ *   rtdm_jpeg_info_get fills it), status[i] (RTDM_OK; RTDM_E_UNSUPPORTED for a stream with
+ *   supported = 0; RTDM_E_INVALID for an unparsable one) and items[i] (its place in the shared
+ *   buffers; all zero unless status[i] is RTDM_OK, so a refused image takes no blocks and has
+ *   no effect on the others).  Block ranges are packed without padding: no workgroup
+ *   straddles two images because workgroups are numbered per image.  out_off / out_pitch
+ *   (each NULL or [n]): byte offset of image i's first pixel from the rgb base pointer given
+ *   to rtdm_jpeg_reconstruct_batch and its row pitch (>= 3 * width; 0 = 3 * width).  With
+ *   out_off NULL the images are packed in index order: back to back when every planned
+ *   image has one size (the arena is then a [N, H, W, 3] tensor, the input rtdm_classify and
+ *   rtdm_letterbox take), else each at the next multiple of 16 bytes.  desc: host memory of
+ *   RTDM_JPEG_BATCH_DESC_BYTES(n) bytes (desc_capacity: its size) that receives the
+ *   device-readable descriptor blob (plain data: per image the plane geometry, sampling
+ *   layout, output placement and the prefix sums that map a workgroup to its image); copy it
+ *   to offset 0 of the staging buffer, or pass the staging buffer itself when it is already
+ *   large enough.  desc NULL: sizes only.  Returns RTDM_OK whenever the arguments are
+ *   well-formed, whatever the per-image statuses; RTDM_E_CAPACITY when desc is too small or
+ *   the batch exceeds 2^31 - 1 workgroups of either kernel.
+ * rtdm_jpeg_entropy_decode_batch: the Huffman stage of every image whose status[i] is
+ *   RTDM_OK on entry, into staging at the plan's offsets, on up to `threads` host threads
+ *   (<= 0: min(n, 16); more than 16: 16), images handed out largest first.  A failing image
+ *   sets status[i], writes its message to messages + i * message_stride (NUL-terminated;
+ *   messages may be NULL) and is marked in the descriptor blob so that the kernels skip it;
+ *   the other images are unaffected.  staging must already hold the descriptor blob.
+ * rtdm_jpeg_reconstruct_batch: staging_dev (device copy of staging[0, staging_bytes)) ->
+ *   pixels at rgb + out_off[i] + y * out_pitch[i] (3 bytes per pixel, RGB, or BGR with
+ *   bgr = 1).  planes: device workspace of layout.workspace_bytes bytes; rgb_bytes: bytes
+ *   addressable from rgb (>= layout.out_bytes).  Asynchronous on the stream, no allocation:
+ *   exactly two launches (dequantisation + IDCT over all blocks; upsampling + colour over
+ *   all pixels, the sampling layout chosen per image inside the kernel).  The descriptor
+ *   blob on the device must be the one the plan wrote for this layout.                  */
+typedef struct rtdm_jpeg_batch_item {
+  int64_t block0;       /* first block of the image in the coefficient arena */
+  int64_t nblocks;      /* = info.nblocks; 0 for a refused image */
+  int64_t plane_off;    /* byte offset of its sample planes in the device workspace */
+  int64_t plane_bytes;
+  int64_t out_off;      /* output placement (given, or the plan's packing) */
+  int64_t out_pitch;
+  int qt_slot;          /* its tables: uint16 [3][64] at qt_offset + qt_slot * 384 */
+  int reserved;
+} rtdm_jpeg_batch_item;
+typedef struct rtdm_jpeg_batch_layout {
+  int n;                   /* images in the batch */
+  int n_planned;           /* images with status RTDM_OK */
+  int64_t nblocks;         /* coefficient arena: nblocks * 64 int16 */
+  int64_t desc_bytes;      /* descriptor blob at offset 0 */
+  int64_t qt_offset;       /* quantisation tables */
+  int64_t coef_offset;     /* coefficient arena */
+  int64_t staging_bytes;   /* all three */
+  int64_t workspace_bytes; /* device sample planes */
+  int64_t out_bytes;       /* bytes the output placement spans from the rgb base */
+  int idct_groups;         /* workgroups of the two launches */
+  int color_groups;
+  int uniform;             /* 1: every planned image has one size */
+  int reserved;
+} rtdm_jpeg_batch_layout;
+#define RTDM_JPEG_BATCH_DESC_BYTES(n) (64 + 192 * (int64_t)(n))
+rtdm_status rtdm_jpeg_batch_plan(const uint8_t* const* data, const int64_t* len, int n, const int64_t* out_off,
+                                 const int64_t* out_pitch, rtdm_jpeg_info* info, int* status,
+                                 rtdm_jpeg_batch_item* items, rtdm_jpeg_batch_layout* layout, void* desc,
+                                 int64_t desc_capacity);
+rtdm_status rtdm_jpeg_entropy_decode_batch(const uint8_t* const* data, const int64_t* len, int n,
+                                           const rtdm_jpeg_batch_item* items, const rtdm_jpeg_batch_layout* layout,
+                                           void* staging, int64_t staging_bytes, int threads, int* status,
+                                           char* messages, int message_stride);
+rtdm_status rtdm_jpeg_reconstruct_batch(const void* staging_dev, const rtdm_jpeg_batch_layout* layout, uint8_t* planes,
+                                        int64_t planes_bytes, uint8_t* rgb, int64_t rgb_bytes, int bgr, void* stream);
 
 #ifdef __cplusplus
 }

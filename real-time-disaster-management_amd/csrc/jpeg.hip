@@ -15,18 +15,9 @@
 // Work: per block 2 x 8 one-dimensional 8-point IDCTs in int32 (the SIMD islow's arithmetic
 // width; the C code's JLONG gives the same values for any coefficient a baseline stream can
 // carry); the kernels are bandwidth-trivial (1.5 bytes per output pixel in, 3 out).
-#include "common.h"
+#include "jpeg_batch.h"
 
 namespace rtdm {
-
-struct JpegPlanes {
-  int ncomp, w, h;
-  int bw[3], bh[3];   // block grids
-  int64_t off[3];     // first block of each component in the coefficient buffer
-  int64_t poff[3];    // byte offset of each component's sample plane (pitch bw * 8)
-  int h_samp[3], v_samp[3], hmax, vmax;
-};
-
 namespace {
 
 constexpr int kCB = 13, kP1 = 2;  // CONST_BITS, PASS1_BITS
@@ -132,6 +123,59 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restric
   }
 }
 
+// jpeg_idct_kernel's body for the batch kernel: one 8x8 block, DEQUANTIZE -> columns (pass 1) ->
+// rows (pass 2) -> range limit -> 8 rows of 8 samples in component c's sample plane (block lb
+// of its grid).  The single-image kernel does not call it: through this helper it allocates
+// 112 VGPRs instead of 99.  Keep the two in step (both are pinned bit-exact against Pillow).
+__device__ __forceinline__ void idct_block(const int16_t* blk, const uint16_t* q,
+                                           const JpegPlanes& p, int c, int64_t lb, uint8_t* planes) {
+  const int by = (int)(lb / p.bw[c]), bx = (int)(lb - (int64_t)by * p.bw[c]);
+  int x[64];
+  {
+    const int4* src = (const int4*)blk;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int4 v = src[k];
+      const int w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        x[8 * k + 2 * e] = (int)(int16_t)(w4[e] & 0xffff);
+        x[8 * k + 2 * e + 1] = (int)(int16_t)((uint32_t)w4[e] >> 16);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 64; ++k) x[k] *= (int)q[k];
+  int ws[64];
+#pragma unroll
+  for (int col = 0; col < 8; ++col) {
+    int o[8];
+    idct8(x[col], x[8 + col], x[16 + col], x[24 + col], x[32 + col], x[40 + col], x[48 + col], x[56 + col], o, true);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) ws[8 * r + col] = o[r];
+  }
+  const int pitch = p.bw[c] * 8;
+  uint8_t* dst = planes + p.poff[c] + ((int64_t)by * 8) * pitch + bx * 8;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    int o[8];
+    const int* w = ws + 8 * r;
+    idct8(w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], o, false);
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      lo |= (uint32_t)idct_limit(o[e]) << (8 * e);
+      hi |= (uint32_t)idct_limit(o[4 + e]) << (8 * e);
+    }
+    *(uint2*)(dst + (int64_t)r * pitch) = make_uint2(lo, hi);
+  }
+}
+
+// the component block b of an image's coefficient range belongs to
+__device__ __forceinline__ int block_comp(const JpegPlanes& p, int64_t b) {
+  return (p.ncomp > 2 && b >= p.off[2]) ? 2 : (p.ncomp > 1 && b >= p.off[1]) ? 1 : 0;
+}
+
 // fancy-upsampled chroma sample (x, y) of plane pl (downsampled size cw x ch, pitch)
 template <int HF, int VF>
 __device__ __forceinline__ int chroma(const uint8_t* __restrict__ pl, int pitch, int cw, int ch, int x, int y) {
@@ -184,26 +228,118 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const uint8_t* __restri
   o[bgr ? 0 : 2] = clamp255(bb);
 }
 
-JpegPlanes planes_of(const rtdm_jpeg_info& in, int64_t* bytes) {
-  JpegPlanes p{};
-  p.ncomp = in.ncomp;
-  p.w = in.width;
-  p.h = in.height;
-  p.hmax = p.vmax = 1;
-  int64_t o = 0;
-  for (int c = 0; c < in.ncomp; ++c) {
-    p.bw[c] = in.bw[c];
-    p.bh[c] = in.bh[c];
-    p.off[c] = in.coef_off[c];
-    p.h_samp[c] = in.h[c];
-    p.v_samp[c] = in.v[c];
-    p.hmax = std::max(p.hmax, in.h[c]);
-    p.vmax = std::max(p.vmax, in.v[c]);
-    p.poff[c] = o;
-    o += (int64_t)in.bw[c] * 8 * in.bh[c] * 8;
+// ---- batch: every image of a descriptor blob (jpeg_batch.h) in one launch per stage ----
+
+// the image workgroup g belongs to: the last one whose first workgroup is <= g (uniform)
+template <bool COLOR>
+__device__ __forceinline__ int batch_image(const JpegBatchImage* __restrict__ im, int n, int g) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((COLOR ? im[mid].color_wg0 : im[mid].idct_wg0) <= g)
+      lo = mid;
+    else
+      hi = mid - 1;
   }
-  if (bytes) *bytes = o;
-  return p;
+  return lo;
+}
+
+// staging: [descriptors | qt | coef] as rtdm_jpeg_batch_plan laid it out
+__global__ __launch_bounds__(kJpegIdctWG) void jpeg_idct_batch_kernel(const uint8_t* __restrict__ staging,
+                                                                      int64_t qt_off, int64_t coef_off,
+                                                                      uint8_t* __restrict__ planes) {
+  const JpegBatchHead* hd = (const JpegBatchHead*)staging;
+  const JpegBatchImage* im = (const JpegBatchImage*)(staging + sizeof(JpegBatchHead));
+  const JpegBatchImage& d = im[batch_image<false>(im, hd->n, (int)blockIdx.x)];
+  if (d.skip) return;
+  const int64_t lb = (int64_t)((int)blockIdx.x - d.idct_wg0) * kJpegIdctWG + threadIdx.x;
+  if (lb < 0 || lb >= d.nblocks) return;
+  const JpegPlanes& p = d.p;  // read in place: a private copy indexed by the component would live in scratch
+  const int64_t b = p.off[0] + lb;
+  const int c = block_comp(p, b);
+  const int16_t* coef = (const int16_t*)(staging + coef_off);
+  const uint16_t* qt = (const uint16_t*)(staging + qt_off) + (int64_t)d.qt_slot * 192;
+  idct_block(coef + b * 64, qt + 64 * c, p, c, b - p.off[c], planes);
+}
+
+// kJpegColorPx horizontally adjacent pixels of one image per thread, stored as whole dwords
+// where the 12 bytes are 4-byte aligned (single bytes otherwise and at a ragged end)
+template <int HF, int VF, bool GRAY>
+__device__ __forceinline__ void color_run(const uint8_t* __restrict__ planes, const JpegBatchImage& d, int bgr,
+                                          uint8_t* __restrict__ rgb, int64_t t) {
+  static_assert(kJpegColorPx == 4, "three dwords carry four pixels");
+  const int w = d.p.w, h = d.p.h;
+  int y, x, nv;
+  if (d.flat) {  // rows are contiguous: a run may continue on the next row
+    const int64_t i0 = t * 4, npx = (int64_t)w * h;
+    if (i0 >= npx) return;
+    y = (int)(i0 / w);
+    x = (int)(i0 - (int64_t)y * w);
+    nv = (int)(npx - i0 < 4 ? npx - i0 : 4);
+  } else {
+    const int runs = (w + 3) >> 2;
+    y = (int)(t / runs);
+    if (y >= h) return;
+    x = (int)(t - (int64_t)y * runs) * 4;
+    nv = w - x < 4 ? w - x : 4;
+  }
+  uint8_t* o = rgb + d.out_off + (int64_t)y * d.out_pitch + 3 * x;
+  const int py = d.p.bw[0] * 8;
+  const uint8_t* yp = planes + d.p.poff[0];
+  uint32_t px[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (e < nv) {
+      const int yv = yp[(int64_t)y * py + x];
+      if constexpr (GRAY) {  // grayscale: the three channels of cv2.imread's BGR image
+        px[e] = (uint32_t)yv * 0x010101u;
+      } else {
+        const int cb = chroma<HF, VF>(planes + d.p.poff[1], d.p.bw[1] * 8, d.cw, d.ch, x, y) - 128;
+        const int cr = chroma<HF, VF>(planes + d.p.poff[2], d.p.bw[2] * 8, d.cw, d.ch, x, y) - 128;
+        const uint32_t r = clamp255(yv + ((91881 * cr + 32768) >> 16));
+        const uint32_t g = clamp255(yv + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+        const uint32_t bb = clamp255(yv + ((116130 * cb + 32768) >> 16));
+        px[e] = bgr ? (bb | (g << 8) | (r << 16)) : (r | (g << 8) | (bb << 16));
+      }
+      if (++x == w) {
+        x = 0;
+        ++y;
+      }
+    }
+  }
+  if (nv == 4 && (((uintptr_t)o) & 3) == 0) {
+    uint32_t* o4 = (uint32_t*)o;
+    o4[0] = px[0] | (px[1] << 24);
+    o4[1] = (px[1] >> 8) | (px[2] << 16);
+    o4[2] = (px[2] >> 16) | (px[3] << 8);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (e < nv) {
+        o[3 * e] = (uint8_t)px[e];
+        o[3 * e + 1] = (uint8_t)(px[e] >> 8);
+        o[3 * e + 2] = (uint8_t)(px[e] >> 16);
+      }
+    }
+  }
+}
+
+// the sampling layout is the image's, so uniform over the workgroup
+__global__ __launch_bounds__(kJpegColorWG) void jpeg_color_batch_kernel(const uint8_t* __restrict__ staging,
+                                                                        const uint8_t* __restrict__ planes, int bgr,
+                                                                        uint8_t* __restrict__ rgb) {
+  const JpegBatchHead* hd = (const JpegBatchHead*)staging;
+  const JpegBatchImage* im = (const JpegBatchImage*)(staging + sizeof(JpegBatchHead));
+  const JpegBatchImage& d = im[batch_image<true>(im, hd->n, (int)blockIdx.x)];
+  if (d.skip || (int)blockIdx.x < d.color_wg0) return;
+  const int64_t t = (int64_t)((int)blockIdx.x - d.color_wg0) * kJpegColorWG + threadIdx.x;
+  switch (d.mode) {
+    case JPEG_GRAY: color_run<1, 1, true>(planes, d, bgr, rgb, t); break;
+    case JPEG_444: color_run<1, 1, false>(planes, d, bgr, rgb, t); break;
+    case JPEG_H2V1: color_run<2, 1, false>(planes, d, bgr, rgb, t); break;
+    case JPEG_H2V2: color_run<2, 2, false>(planes, d, bgr, rgb, t); break;
+    default: break;
+  }
 }
 
 }  // namespace
@@ -257,6 +393,32 @@ rtdm_status rtdm_jpeg_reconstruct(const int16_t* coef, const uint16_t* qt, const
       hipLaunchKernelGGL((jpeg_color_kernel<2, 1>), g, dim3(256), 0, s, planes, p, bgr, rgb, pitch);
     else
       hipLaunchKernelGGL((jpeg_color_kernel<1, 1>), g, dim3(256), 0, s, planes, p, bgr, rgb, pitch);
+    RTDM_HIP(hipGetLastError());
+  });
+}
+
+rtdm_status rtdm_jpeg_reconstruct_batch(const void* staging_dev, const rtdm_jpeg_batch_layout* layout, uint8_t* planes,
+                                        int64_t planes_bytes, uint8_t* rgb, int64_t rgb_bytes, int bgr, void* stream) {
+  return guard([&] {
+    RTDM_REQUIRE(staging_dev && layout && planes && rgb, RTDM_E_INVALID, "jpeg_reconstruct_batch: NULL pointer");
+    const rtdm_jpeg_batch_layout& l = *layout;
+    RTDM_REQUIRE(l.n >= 0 && l.n_planned >= 0 && l.n_planned <= l.n && l.nblocks >= 0 && l.idct_groups >= 0 &&
+                     l.color_groups >= 0 && l.desc_bytes == RTDM_JPEG_BATCH_DESC_BYTES(l.n) &&
+                     l.qt_offset >= l.desc_bytes && l.qt_offset % 16 == 0 &&
+                     l.coef_offset >= l.qt_offset + 384ll * l.n && l.coef_offset % 16 == 0 &&
+                     l.staging_bytes == l.coef_offset + l.nblocks * 128,
+                 RTDM_E_INVALID, "jpeg_reconstruct_batch: layout was not made by rtdm_jpeg_batch_plan");
+    RTDM_REQUIRE(((uintptr_t)staging_dev & 15) == 0, RTDM_E_INVALID, "jpeg_reconstruct_batch: staging must be 16-byte aligned");
+    RTDM_REQUIRE(planes_bytes >= l.workspace_bytes, RTDM_E_CAPACITY, "jpeg_reconstruct_batch: workspace too small");
+    RTDM_REQUIRE(rgb_bytes >= l.out_bytes, RTDM_E_CAPACITY, "jpeg_reconstruct_batch: output too small");
+    if (l.n_planned == 0 || l.idct_groups == 0 || l.color_groups == 0) return;  // nothing decodable in the batch
+    hipStream_t s = (hipStream_t)stream;
+    const uint8_t* st = (const uint8_t*)staging_dev;
+    hipLaunchKernelGGL(jpeg_idct_batch_kernel, dim3((unsigned)l.idct_groups), dim3(kJpegIdctWG), 0, s, st, l.qt_offset,
+                       l.coef_offset, planes);
+    RTDM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_color_batch_kernel, dim3((unsigned)l.color_groups), dim3(kJpegColorWG), 0, s, st,
+                       (const uint8_t*)planes, bgr, rgb);
     RTDM_HIP(hipGetLastError());
   });
 }

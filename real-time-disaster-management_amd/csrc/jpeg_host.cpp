@@ -12,11 +12,19 @@
 // leaves room: a marker or the end of data inside the entropy-coded segment reads as zero
 // bits, the AC run index past 63 clamps to 63 (jpeg_natural_order's guard entries), the DC
 // predictor is an int that the JCOEF store truncates.
+//
+// The batch entry points (rtdm_jpeg_batch_plan, rtdm_jpeg_entropy_decode_batch) run the same
+// parser and decoder per image, the Huffman stage on a pool of std::threads: the images share
+// nothing but the read-only kNatural table, and each writes only its own slots of the staging
+// buffer.
 #include <algorithm>
+#include <atomic>
 #include <cstring>
+#include <string>
+#include <thread>
 #include <vector>
 
-#include "common.h"
+#include "jpeg_batch.h"
 
 namespace rtdm {
 namespace {
@@ -38,6 +46,13 @@ struct Huff {
 };
 
 void build_huff(Huff& h, const uint8_t* counts, const uint8_t* vals, int nvals) {
+  h.ok = false;
+  // an over-subscribed table (more codes of a length than its bits can number) is refused
+  // before anything is written: its look[] entries would land past the table
+  for (int len = 1, code = 0; len <= 16; ++len, code <<= 1) {
+    code += counts[len - 1];
+    RTDM_REQUIRE(code <= (1 << len), RTDM_E_INVALID, "jpeg: bad Huffman table");
+  }
   std::memcpy(h.vals, vals, nvals);
   for (int i = 0; i < (1 << kLook); ++i) h.look[i] = -1;
   int code = 0, k = 0;
@@ -55,7 +70,6 @@ void build_huff(Huff& h, const uint8_t* counts, const uint8_t* vals, int nvals) 
     } else {
       h.maxcode[len] = -1;
     }
-    RTDM_REQUIRE(code <= (1 << len), RTDM_E_INVALID, "jpeg: bad Huffman table");
     code <<= 1;
   }
   h.maxcode[17] = 0x7fffffff;
@@ -233,6 +247,11 @@ void parse_dht(Jpeg& j, Reader& r) {
     RTDM_REQUIRE(nv <= 256, RTDM_E_INVALID, "jpeg: bad Huffman table");
     uint8_t vals[256];
     for (int i = 0; i < nv; ++i) vals[i] = r.u8();
+    RTDM_REQUIRE((tc >> 4) <= 1 && (tc & 15) <= 3, RTDM_E_INVALID, "jpeg: bad Huffman table class / index");
+    // a DC symbol is the bit count of the difference that follows: above 15 it would shift the
+    // bit reader's 64-bit accumulator by a negative amount (libjpeg refuses such a table too)
+    if ((tc >> 4) == 0)
+      for (int i = 0; i < nv; ++i) RTDM_REQUIRE(vals[i] <= 15, RTDM_E_INVALID, "jpeg: bad Huffman table");
     build_huff((tc >> 4) ? j.ac[tc & 3] : j.dc[tc & 3], counts, vals, nv);
   }
 }
@@ -338,8 +357,9 @@ Jpeg walk(const uint8_t* data, int64_t len, int16_t* coef, int64_t nblocks) {
         for (int i = 0; i < j.nc; ++i)
           if (j.c[i].id == id) ci = i;
         RTDM_REQUIRE(ci >= 0, RTDM_E_INVALID, "jpeg: scan names an unknown component");
+        RTDM_REQUIRE((t >> 4) <= 3 && (t & 15) <= 3, RTDM_E_INVALID, "jpeg: scan names Huffman table above 3");
         j.c[ci].td = t >> 4;
-        j.c[ci].ta = t & 3;
+        j.c[ci].ta = t & 15;
         sc[k] = ci;
       }
       const int ss = r.u8(), se = r.u8(), a = r.u8();
@@ -370,7 +390,19 @@ void fill_info(const Jpeg& j, rtdm_jpeg_info* info) {
     info->coef_off[i] = j.c[i].off;
   }
   info->nblocks = j.nblocks;
-  info->supported = j.unsupported ? 0 : 1;
+  // ... and only the sampling layouts the reconstruct kernels take (4:4:0, 4:1:1, ... are refused)
+  info->supported = (j.unsupported || jpeg_mode(info->ncomp, info->h, info->v) < 0) ? 0 : 1;
+}
+
+// the single-image entropy decode on caller-owned buffers (shared by both entry points)
+void entropy_decode_into(const uint8_t* data, int64_t len, int16_t* coef, int64_t nblocks, uint16_t* qt,
+                         rtdm_jpeg_info* info) {
+  const Jpeg j = walk(data, len, coef, nblocks);
+  for (int i = 0; i < j.nc; ++i) {
+    RTDM_REQUIRE(j.qok[j.c[i].tq], RTDM_E_INVALID, "jpeg: missing quantisation table");
+    std::memcpy(qt + 64 * i, j.q[j.c[i].tq], 64 * sizeof(uint16_t));
+  }
+  if (info) fill_info(j, info);
 }
 
 }  // namespace
@@ -391,12 +423,196 @@ rtdm_status rtdm_jpeg_entropy_decode(const uint8_t* data, int64_t len, int16_t* 
                                      rtdm_jpeg_info* info) {
   return guard([&] {
     RTDM_REQUIRE(coef && qt, RTDM_E_INVALID, "jpeg_entropy_decode: NULL buffer");
-    const Jpeg j = walk(data, len, coef, nblocks);
-    for (int i = 0; i < j.nc; ++i) {
-      RTDM_REQUIRE(j.qok[j.c[i].tq], RTDM_E_INVALID, "jpeg: missing quantisation table");
-      std::memcpy(qt + 64 * i, j.q[j.c[i].tq], 64 * sizeof(uint16_t));
+    entropy_decode_into(data, len, coef, nblocks, qt, info);
+  });
+}
+
+rtdm_status rtdm_jpeg_batch_plan(const uint8_t* const* data, const int64_t* len, int n, const int64_t* out_off,
+                                 const int64_t* out_pitch, rtdm_jpeg_info* info, int* status,
+                                 rtdm_jpeg_batch_item* items, rtdm_jpeg_batch_layout* layout, void* desc,
+                                 int64_t desc_capacity) {
+  return guard([&] {
+    RTDM_REQUIRE(n >= 0 && (n == 0 || (data && len)) && info && status && items && layout, RTDM_E_INVALID,
+                 "jpeg_batch_plan: NULL pointer");
+    RTDM_REQUIRE(n <= (1 << 24), RTDM_E_CAPACITY, "jpeg_batch_plan: batch too large");
+    rtdm_jpeg_batch_layout l{};
+    l.n = n;
+    l.desc_bytes = RTDM_JPEG_BATCH_DESC_BYTES(n);
+    RTDM_REQUIRE(!desc || desc_capacity >= l.desc_bytes, RTDM_E_CAPACITY, "jpeg_batch_plan: descriptor buffer too small");
+    JpegBatchHead* hd = (JpegBatchHead*)desc;
+    JpegBatchImage* im = desc ? (JpegBatchImage*)((uint8_t*)desc + sizeof(JpegBatchHead)) : nullptr;
+    if (desc) std::memset(desc, 0, (size_t)l.desc_bytes);
+    // headers
+    l.uniform = 1;
+    int w0 = 0, h0 = 0;
+    for (int i = 0; i < n; ++i) {
+      std::memset(&info[i], 0, sizeof(info[i]));
+      std::memset(&items[i], 0, sizeof(items[i]));
+      try {
+        fill_info(walk(data[i], len[i], nullptr, 0), &info[i]);
+        status[i] = info[i].supported ? RTDM_OK : RTDM_E_UNSUPPORTED;
+      } catch (const Error& e) {
+        status[i] = e.code;
+      }
+      if (status[i] != RTDM_OK) continue;
+      if (l.n_planned++ == 0) {
+        w0 = info[i].width;
+        h0 = info[i].height;
+      } else if (info[i].width != w0 || info[i].height != h0) {
+        l.uniform = 0;
+      }
     }
-    if (info) fill_info(j, info);
+    if (l.n_planned == 0) l.uniform = 0;
+    // placement
+    int64_t idct_wg = 0, color_wg = 0, next_out = 0;
+    for (int i = 0; i < n; ++i) {
+      if (im) {
+        im[i].idct_wg0 = (int32_t)idct_wg;
+        im[i].color_wg0 = (int32_t)color_wg;
+        im[i].skip = 1;
+      }
+      if (status[i] != RTDM_OK) continue;
+      const rtdm_jpeg_info& in = info[i];
+      rtdm_jpeg_batch_item& it = items[i];
+      int64_t pbytes = 0;
+      JpegPlanes p = planes_of(in, &pbytes);
+      bool ok = in.nblocks > 0;
+      for (int c = 0; c < in.ncomp; ++c)
+        ok = ok && in.bw[c] > 0 && in.bh[c] > 0 && in.bw[c] * 8 >= (in.width * in.h[c] + p.hmax - 1) / p.hmax &&
+             in.bh[c] * 8 >= (in.height * in.v[c] + p.vmax - 1) / p.vmax;
+      const int64_t pitch = out_pitch && out_pitch[i] ? out_pitch[i] : 3ll * in.width;
+      const int64_t off = out_off ? out_off[i] : next_out;
+      if (!ok || pitch < 3ll * in.width || off < 0) {  // a placement the kernels cannot honour
+        status[i] = RTDM_E_INVALID;
+        --l.n_planned;
+        continue;
+      }
+      it.block0 = l.nblocks;
+      it.nblocks = in.nblocks;
+      it.plane_off = l.workspace_bytes;
+      it.plane_bytes = pbytes;
+      it.out_off = off;
+      it.out_pitch = pitch;
+      it.qt_slot = i;
+      const int64_t span = (int64_t)(in.height - 1) * pitch + 3ll * in.width;
+      l.out_bytes = std::max(l.out_bytes, off + span);
+      next_out = off + span;
+      if (!l.uniform) next_out = round_up(next_out, 16);
+      const bool flat = pitch == 3ll * in.width;
+      const int64_t runs = flat ? ((int64_t)in.width * in.height + kJpegColorPx - 1) / kJpegColorPx
+                                : (int64_t)in.height * ((in.width + kJpegColorPx - 1) / kJpegColorPx);
+      if (im) {
+        JpegBatchImage& d = im[i];
+        for (int c = 0; c < in.ncomp; ++c) {
+          p.off[c] += it.block0;
+          p.poff[c] += it.plane_off;
+        }
+        d.p = p;
+        d.nblocks = in.nblocks;
+        d.out_off = off;
+        d.out_pitch = pitch;
+        d.qt_slot = it.qt_slot;
+        d.mode = jpeg_mode(in.ncomp, in.h, in.v);
+        d.flat = flat ? 1 : 0;
+        d.skip = 0;
+        d.cw = in.ncomp == 3 ? (in.width * in.h[1] + p.hmax - 1) / p.hmax : in.width;
+        d.ch = in.ncomp == 3 ? (in.height * in.v[1] + p.vmax - 1) / p.vmax : in.height;
+      }
+      l.nblocks += in.nblocks;
+      l.workspace_bytes += round_up(pbytes, 16);
+      idct_wg += (in.nblocks + kJpegIdctWG - 1) / kJpegIdctWG;
+      color_wg += (runs + kJpegColorWG - 1) / kJpegColorWG;
+    }
+    RTDM_REQUIRE(idct_wg < (1ll << 31) - 1 && color_wg < (1ll << 31) - 1, RTDM_E_CAPACITY,
+                 "jpeg_batch_plan: batch exceeds 2^31 - 1 workgroups");
+    l.idct_groups = (int)idct_wg;
+    l.color_groups = (int)color_wg;
+    l.qt_offset = round_up(l.desc_bytes, 256);
+    l.coef_offset = round_up(l.qt_offset + 384ll * n, 256);
+    l.staging_bytes = l.coef_offset + l.nblocks * 128;
+    if (hd) {
+      hd->n = n;
+      hd->idct_groups = l.idct_groups;
+      hd->color_groups = l.color_groups;
+    }
+    *layout = l;
+  });
+}
+
+rtdm_status rtdm_jpeg_entropy_decode_batch(const uint8_t* const* data, const int64_t* len, int n,
+                                           const rtdm_jpeg_batch_item* items, const rtdm_jpeg_batch_layout* layout,
+                                           void* staging, int64_t staging_bytes, int threads, int* status,
+                                           char* messages, int message_stride) {
+  return guard([&] {
+    RTDM_REQUIRE(n >= 0 && (n == 0 || (data && len)) && items && layout && staging && status, RTDM_E_INVALID,
+                 "jpeg_entropy_decode_batch: NULL pointer");
+    const rtdm_jpeg_batch_layout& l = *layout;
+    RTDM_REQUIRE(l.n == n && l.desc_bytes == RTDM_JPEG_BATCH_DESC_BYTES(n) && l.qt_offset >= l.desc_bytes &&
+                     l.coef_offset >= l.qt_offset + 384ll * n && l.nblocks >= 0 &&
+                     l.staging_bytes == l.coef_offset + l.nblocks * 128,
+                 RTDM_E_INVALID, "jpeg_entropy_decode_batch: layout was not made by rtdm_jpeg_batch_plan");
+    RTDM_REQUIRE(staging_bytes >= l.staging_bytes, RTDM_E_CAPACITY, "jpeg_entropy_decode_batch: staging buffer too small");
+    RTDM_REQUIRE(!messages || message_stride > 0, RTDM_E_INVALID, "jpeg_entropy_decode_batch: bad message stride");
+    uint8_t* st = (uint8_t*)staging;
+    const JpegBatchHead* hd = (const JpegBatchHead*)st;
+    JpegBatchImage* im = (JpegBatchImage*)(st + sizeof(JpegBatchHead));
+    RTDM_REQUIRE(hd->n == n, RTDM_E_INVALID, "jpeg_entropy_decode_batch: staging does not hold the plan's descriptors");
+    // every planned image's slots lie inside the arena (checked before any thread writes)
+    std::vector<int> order;
+    for (int i = 0; i < n; ++i) {
+      if (messages) messages[(int64_t)i * message_stride] = 0;
+      if (status[i] != RTDM_OK) continue;
+      const rtdm_jpeg_batch_item& it = items[i];
+      RTDM_REQUIRE(it.nblocks > 0 && it.block0 >= 0 && it.block0 + it.nblocks <= l.nblocks && it.qt_slot >= 0 && it.qt_slot < n,
+                   RTDM_E_INVALID, "jpeg_entropy_decode_batch: item outside the layout");
+      order.push_back(i);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return items[a].nblocks > items[b].nblocks; });
+    auto one = [&](int i) {
+      const rtdm_jpeg_batch_item& it = items[i];
+      int16_t* coef = (int16_t*)(st + l.coef_offset) + it.block0 * 64;
+      uint16_t* qt = (uint16_t*)(st + l.qt_offset) + (int64_t)it.qt_slot * 192;
+      int code = RTDM_OK;
+      const char* msg = "";
+      std::string keep;
+      try {
+        entropy_decode_into(data[i], len[i], coef, it.nblocks, qt, nullptr);
+      } catch (const Error& e) {
+        code = e.code;
+        keep = e.msg;
+        msg = keep.c_str();
+      } catch (...) {
+        code = RTDM_E_INVALID;
+        msg = "jpeg: entropy decode failed";
+      }
+      if (code == RTDM_OK) return;
+      status[i] = code;
+      im[i].skip = 1;
+      if (messages) {
+        char* m = messages + (int64_t)i * message_stride;
+        std::strncpy(m, msg, (size_t)message_stride - 1);
+        m[message_stride - 1] = 0;
+      }
+    };
+    const int todo = (int)order.size();
+    int nt = threads <= 0 ? std::min(n, 16) : std::min(threads, 16);  // a command may use 16 CPUs
+    nt = std::max(1, std::min(nt, todo));
+    std::atomic<int> next{0};
+    auto work = [&] {
+      for (int k = next.fetch_add(1); k < todo; k = next.fetch_add(1)) one(order[k]);
+    };
+    if (nt == 1) {
+      work();
+      return;
+    }
+    std::vector<std::thread> pool;
+    pool.reserve(nt - 1);
+    try {
+      for (int t = 0; t < nt - 1; ++t) pool.emplace_back(work);
+    } catch (...) {  // no more threads: the ones that started (and this one) finish the queue
+    }
+    work();
+    for (auto& t : pool) t.join();
   });
 }
 

@@ -61,6 +61,23 @@ class rtdm_jpeg_info(ctypes.Structure):
                 ("supported", c_int)]
 
 
+class rtdm_jpeg_batch_item(ctypes.Structure):
+    _fields_ = [("block0", c_int64), ("nblocks", c_int64), ("plane_off", c_int64), ("plane_bytes", c_int64),
+                ("out_off", c_int64), ("out_pitch", c_int64), ("qt_slot", c_int), ("reserved", c_int)]
+
+
+class rtdm_jpeg_batch_layout(ctypes.Structure):
+    _fields_ = [("n", c_int), ("n_planned", c_int), ("nblocks", c_int64), ("desc_bytes", c_int64),
+                ("qt_offset", c_int64), ("coef_offset", c_int64), ("staging_bytes", c_int64),
+                ("workspace_bytes", c_int64), ("out_bytes", c_int64), ("idct_groups", c_int), ("color_groups", c_int),
+                ("uniform", c_int), ("reserved", c_int)]
+
+
+def jpeg_batch_desc_bytes(n: int) -> int:
+    """RTDM_JPEG_BATCH_DESC_BYTES(n)"""
+    return 64 + 192 * int(n)
+
+
 # name -> (restype, argtypes); must match include/rtdm.h exactly
 SIGNATURES = {
     "rtdm_abi_version": (c_int, []),
@@ -111,6 +128,14 @@ SIGNATURES = {
     "rtdm_jpeg_workspace_bytes": (c_int64, [POINTER(rtdm_jpeg_info)]),
     "rtdm_jpeg_reconstruct": (c_int, [c_void_p, c_void_p, POINTER(rtdm_jpeg_info), c_void_p, c_int64, c_void_p, c_int64,
                                       c_int, c_void_p]),
+    "rtdm_jpeg_batch_plan": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, POINTER(rtdm_jpeg_info),
+                                     POINTER(c_int), POINTER(rtdm_jpeg_batch_item), POINTER(rtdm_jpeg_batch_layout),
+                                     c_void_p, c_int64]),
+    "rtdm_jpeg_entropy_decode_batch": (c_int, [c_void_p, c_void_p, c_int, POINTER(rtdm_jpeg_batch_item),
+                                               POINTER(rtdm_jpeg_batch_layout), c_void_p, c_int64, c_int,
+                                               POINTER(c_int), c_void_p, c_int]),
+    "rtdm_jpeg_reconstruct_batch": (c_int, [c_void_p, POINTER(rtdm_jpeg_batch_layout), c_void_p, c_int64, c_void_p,
+                                            c_int64, c_int, c_void_p]),
 }
 
 _lib = None

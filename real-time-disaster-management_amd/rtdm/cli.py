@@ -57,6 +57,28 @@ def load_image(path: str, device) -> torch.Tensor:
     return torch.from_numpy(read_image_rgb(path)).to(device)
 
 
+def load_images(paths, device) -> list:
+    """load_image for a list of files, in path order: every baseline JPEG goes through ONE
+    rtdm.jpeg.decode_batch call (threaded Huffman stage, one copy, two launches); the rest
+    (PNG, progressive JPEG, ...) decode through Pillow as in load_image."""
+    from . import jpeg
+    frames, batch, slots = [None] * len(paths), [], []
+    for i, path in enumerate(paths):
+        if not os.path.exists(path):
+            raise ValueError(f"Could not load image at {path}")
+        with open(path, "rb") as f:
+            data = f.read()
+        if data[:2] == b"\xff\xd8" and jpeg.supported(data):
+            batch.append(data)
+            slots.append(i)
+        else:
+            frames[i] = torch.from_numpy(read_image_rgb(path)).to(device)
+    if batch:
+        for i, frame in zip(slots, jpeg.decode_batch(batch, device)):
+            frames[i] = frame
+    return frames
+
+
 def list_images(source: str):
     if os.path.isdir(source):
         return sorted(os.path.join(source, f) for f in os.listdir(source) if f.lower().endswith(IMG_EXTS))
